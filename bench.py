@@ -10,6 +10,9 @@ and outputs resident in HBM.  ONE JSON line from rank 0:
   roofline              the dominant kernel timed by HIP events attached to each of its dispatches inside the timed region,
                         against the resource that binds it (LDS row-gather rate for the scans, the issue/latency floor of
                         ivf_fused_kernel for the inverted index, HBM for the single-query Deep scan)
+
+A plain run stops there: set-up, pre-heat, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR` writes the rows the last
+timed step returned (ids.npy, dists.npy; counts.npy for the inverted index).  Everything below runs under `--full` only:
   cpu_baseline          the real reference build (oracle/_ref; else the C oracle) on this box's host cores, same index and
                         queries, with `ids_match_gpu`; rank 0, N=1 only
   others                (default invocation, N=1) EVERY other BASELINE config measured in the same process: configs[2] `ivf`,
@@ -97,7 +100,42 @@ def parse():
                          "printed on stdout is the compact form")
     ap.add_argument("--scan-mode", type=int, default=1, choices=[0, 1],
                     help="1: 8-bit filter + exact re-rank (default), 0: exact scan of every code; identical results")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: cold start, uninstrumented / device-resident / sync-call / host-call / "
+                         "fresh-query / two-stream loops, per-kernel shares, live counters, recall, the CPU baseline, `others` (the other "
+                         "BASELINE configs), with_gather and strong scaling at N > 1, and the long form of the line.  Off: set up, "
+                         "warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / "
+                         "float64; ids as float64)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: the side measurements these switches name belong to --full
+        args.no_cpu_baseline = args.no_host_call = args.no_fresh = args.no_live_counters = True
+        args.no_pipelined = args.no_others = args.no_strong = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array with one row per query} -> path/<name>.npy, integers as float64 and floats as float32.  Above
+    DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rows is written instead, with its row numbers in rows.npy."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64) if a.dtype.kind in "iub" else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    n_rows = min(a.shape[0] for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, int(n_rows * DUMP_LIMIT_BYTES // total) - 1)
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def emit(line, args):
@@ -107,12 +145,15 @@ def emit(line, args):
     from rii_amd import benchline
     path = args.full_out or os.path.join(ROOT, "gpurun_out", "bench_full_%s.json" % args.workload.replace("-", "_"))
     shown = None
+    if not (args.full or args.full_out):
+        path = None                                  # (a plain run's line is short: no long form)
     try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(line, f)
-            f.write("\n")
-        shown = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
+        if path is not None:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(line, f)
+                f.write("\n")
+            shown = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
     except OSError:
         pass                                     # a read-only tree must not cost the run its line
     # RCCL prints its version banner through C stdio, which is fully buffered when stdout is a pipe: left alone it comes out at
@@ -395,9 +436,10 @@ def preheat_count(step, sync, count):
     return count
 
 
-def measure(eng, step, steps, warmup, barrier, sync, heat=True):
+def measure(eng, step, steps, warmup, barrier, sync, heat=True, breakdown=True, after_timed=None):
     """pre-heat (clock ramp), W warm-up steps, K timed steps with ONLY the dominant kernel carrying HIP events (attached to its
-    dispatch: engine option `timing` = 2), then a short untimed pass with events around every launch for the other kernels' shares."""
+    dispatch: engine option `timing` = 2), then (`breakdown`) a short untimed pass with events around every launch for the other
+    kernels' shares.  `after_timed` is called right after the timed steps."""
     if heat is True:
         preheat(step, sync)
     elif heat:
@@ -408,9 +450,13 @@ def measure(eng, step, steps, warmup, barrier, sync, heat=True):
     eng.set_option("timing", 2)
     eng.timing_reset()
     elapsed = timed_loop(step, steps, barrier)
+    if after_timed is not None:
+        after_timed()
     eng.set_option("timing", 0)
     dom = {kn: eng.timing_read(kn) for kn in DOMINANT}
     eng.timing_reset()
+    if not breakdown:
+        return elapsed, dom, {}
     eng.set_option("timing", 1)
     n_break = max(3, min(steps, 10))
     for _ in range(n_break):
@@ -918,7 +964,8 @@ def ref_harness_workload(args, torch, dev, arch, barrier, base_codes_src):
     return obj
 
 
-def deep_ivf_on(eng, comm, args, torch, dev, barrier, q, n_shard, n_global, rank, world, nlist, L, topk, steps, cw, codes, arch):
+def deep_ivf_on(eng, comm, args, torch, dev, barrier, q, n_shard, n_global, rank, world, nlist, L, topk, steps, cw, codes, arch,
+                rows_out=None):
     """The database-sharded inverted index over this rank's Deep1B-shaped shard, ONE rii_query_ivf_dbsharded_dev call per step (list
     lengths -> all-gather -> ivf_shard kernel -> pack -> all-gather -> merge -> finish).  Lists: modulo_lists() over the local ids,
     centres: nlist random codes, the same on every rank.  -> (object, rows)"""
@@ -935,7 +982,11 @@ def deep_ivf_on(eng, comm, args, torch, dev, barrier, q, n_shard, n_global, rank
         comm.query_ivf_dbsharded_dev(eng, rank * n_shard, n_global, q.data_ptr(), B, topk, 0, 0, 0, L, oi.data_ptr(), od.data_ptr(),
                                      oc.data_ptr(), 0, stream)
 
-    elapsed, dom, shares = measure(eng, step, steps, 2, barrier, torch.cuda.synchronize, heat=8)
+    def keep_rows():                                 # (rows_out: the rows of the last timed step)
+        if rows_out is not None:
+            rows_out.update(ids=oi.cpu().numpy(), dists=od.cpu().numpy(), counts=oc.cpu().numpy())
+
+    elapsed, dom, shares = measure(eng, step, steps, 2, barrier, torch.cuda.synchronize, heat=8, after_timed=keep_rows)
     plain = timed_loop(step, steps, barrier)
     k_ms, k_n = dom["ivf_shard"]
     c_ms, c_n = dom["shard_coarse"]
@@ -1004,7 +1055,13 @@ def main_deep_ivf(args, world, rank, local, dev, arch):
             dist.barrier()
         torch.cuda.synchronize()
 
-    obj = deep_ivf_on(eng, comm, args, torch, dev, barrier, q, n_shard, n_global, rank, world, nlist, L, args.topk, args.steps, cw, codes, arch)
+    rows = {}
+    obj = deep_ivf_on(eng, comm, args, torch, dev, barrier, q, n_shard, n_global, rank, world, nlist, L, args.topk, args.steps, cw, codes, arch,
+                      rows_out=rows)
+    if args.dump_outputs and rank == 0:
+        past = np.arange(args.topk)[None, :] >= rows["counts"][:, None]
+        dump_outputs(args.dump_outputs, {"ids": np.where(past, -1, rows["ids"]), "dists": np.where(past, np.float32(np.inf), rows["dists"]),
+                                         "counts": rows["counts"]})
     elapsed_ms = obj["ms_per_step"]
     if use_dist:
         t = torch.tensor([elapsed_ms], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
@@ -1066,8 +1123,12 @@ def main_deep(args, world, rank, local, dev, arch):
         torch.cuda.synchronize()
 
     # (the step holds a collective: pre-heat by step count, the same on every rank)
+    def keep_rows():
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"ids": merged[0][0].cpu().numpy(), "dists": merged[0][1].cpu().numpy()})
+
     elapsed, dom, shares = measure(eng, step, args.steps, args.warmup, barrier, torch.cuda.synchronize,
-                                   heat=max(8, min(200, int(0.15 / max(1e-4, 2e-10 * n_shard * B / 1024.0)))))
+                                   heat=max(8, min(200, int(0.15 / max(1e-4, 2e-10 * n_shard * B / 1024.0)))), after_timed=keep_rows)
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1144,11 +1205,10 @@ def main():
         base, train, query = bd.sift_like(n_base=N, n_train=100_000, n_query=max(10_000, nq), D=D)
         cw = bd.train_pq(train, M, Ks, iters=10, seed=123, device=dev)
         codes = bd.encode_pq(base, cw, device=dev)
-        gt = bd.exact_nn(base, query[:nq], device=dev)
         t_cw = torch.from_numpy(cw).to(dev)
         t_codes = torch.from_numpy(codes).to(dev)
         t_q = torch.from_numpy(np.ascontiguousarray(query[:nq])).to(dev)
-        t_gt = torch.from_numpy(gt).to(dev)
+        t_gt = torch.from_numpy(bd.exact_nn(base, query[:nq], device=dev)).to(dev) if args.full else None     # (recall: --full)
         # (the `others.ref_harness` leg re-encodes the same vectors with M = 64: kept for the default invocation only)
         keep_vectors = (base, train, query) if (world == 1 and not args.no_others and args.workload == "linear" and args.topk == 1) else None
         del base, train
@@ -1156,11 +1216,13 @@ def main():
         t_cw = torch.empty((M, Ks, D // M), dtype=torch.float32, device=dev)
         t_codes = torch.empty((N, M), dtype=torch.uint8, device=dev)
         t_q = torch.empty((nq, D), dtype=torch.float32, device=dev)
-        t_gt = torch.empty((nq,), dtype=torch.int64, device=dev)
+        t_gt = torch.empty((nq,), dtype=torch.int64, device=dev) if args.full else None
     host_coll = use_dist and dist.get_backend() != "nccl"         # gloo: run the collectives on host copies
 
     if use_dist:
         for t in (t_cw, t_codes, t_q, t_gt):
+            if t is None:
+                continue
             if host_coll:
                 c = t.cpu()
                 dist.broadcast(c, 0)
@@ -1171,7 +1233,7 @@ def main():
     codes = t_codes.cpu().numpy()
     del t_codes
     my_q = t_q[rank * B:(rank + 1) * B].contiguous()
-    my_gt = t_gt[rank * B:(rank + 1) * B].cpu().numpy()
+    my_gt = t_gt[rank * B:(rank + 1) * B].cpu().numpy() if args.full else None
 
     # ---------------- engine (one per GPU, index replicated) ----------------
     eng = RiiGpu(cw, False, simd_arch=arch, device=local)
@@ -1245,44 +1307,64 @@ def main():
     if args.latency:
         return main_latency(args, eng, t_q, run, ivf, topk, h_tids, L, rank, world, dev)
 
-    # first exactly what the contract's wording gives from an idle GPU (W warm-up + K timed steps, clocks still ramping) ...
-    for _ in range(args.warmup):
-        step()
-    wall["setup_s"] = time.perf_counter() - t_start          # imports, synthetic data, codebooks, encoding, ground truth, index upload
-    cold = timed_loop(step, args.steps, barrier)
-    # ... then the steady state: pre-heat, W warm-up steps, K timed steps (this is `value`)
-    elapsed, dom, extra = measure(eng, step, args.steps, args.warmup, barrier, torch.cuda.synchronize)
-    last = host_rows[(it_h[0] - 1) & 1]
-    res_ids = last[0].numpy().copy()                 # (host memory: the rows the timed steps delivered)
-    res_cnt = last[2].numpy().copy() if ivf else None
-    rows_both_buffers_equal = bool(np.array_equal(host_rows[0][0].numpy(), host_rows[1][0].numpy()))
-    # the same K steps with no timing event at all (twice): what the events attached to the dominant kernel's dispatches cost,
-    # and how stable a K-step sample is
-    plain = [timed_loop(step, args.steps, barrier) for _ in range(2)]
-    # ... with the rows left in HBM (round 3's `value`), and one synchronous device-queries -> host-rows call per step
-    dev_res = timed_loop(step_dev, args.steps, barrier)
-    assert np.array_equal(out_ids.cpu().numpy(), res_ids), "host-delivered rows differ from the device-resident ones"
-    h_i, h_d, h_c = np.empty((B, topk), np.int64), np.empty((B, topk), np.float32), np.empty(B, np.int64)
-
-    def step_sync():
-        if ivf:
-            eng.query_ivf_dev_to_host(my_q.data_ptr(), B, topk, d_tids, S, L, h_i, h_d, h_c, stream)
-        else:
-            eng.query_linear_dev_to_host(my_q.data_ptr(), B, topk, d_tids, S, h_i, h_d, stream)
-
-    for _ in range(max(args.warmup, 1)):
-        step_sync()
-    sync_call = timed_loop(step_sync, args.steps, barrier)
-    assert np.array_equal(h_i, res_ids)
-    elapsed_g = None
-    if use_dist:
-        preheat_count(step_gather, torch.cuda.synchronize, 100)
+    # first (--full) exactly what the contract's wording gives from an idle GPU (W warm-up + K timed steps, clocks still ramping) ...
+    if args.full:
         for _ in range(args.warmup):
-            step_gather()
-        elapsed_g = timed_loop(step_gather, args.steps, barrier)
-        elapsed, elapsed_g, plain[0], plain[1], cold, dev_res, sync_call = max_over_ranks(elapsed, elapsed_g, plain[0], plain[1], cold, dev_res, sync_call)
-        allq = gathered[0][0]                        # the gathered batch really is every rank's rows, in rank order
-        assert allq.shape[0] == B * world and torch.equal(allq[rank * B:(rank + 1) * B].to(out_ids.device), out_ids)
+            step()
+    wall["setup_s"] = time.perf_counter() - t_start          # imports, synthetic data, codebooks, encoding, ground truth, index upload
+    if args.full:
+        cold = timed_loop(step, args.steps, barrier)
+    # ... then the steady state: pre-heat, W warm-up steps, K timed steps (this is `value`)
+    last_rows = {}
+
+    def keep_last_rows():                            # (host memory: the rows the last timed step delivered)
+        last = host_rows[(it_h[0] - 1) & 1]
+        last_rows["ids"], last_rows["dists"] = last[0].numpy().copy(), last[1].numpy().copy()
+        if ivf:
+            last_rows["counts"] = last[2].numpy().copy()
+
+    elapsed, dom, extra = measure(eng, step, args.steps, args.warmup, barrier, torch.cuda.synchronize, breakdown=args.full,
+                                  after_timed=keep_last_rows)
+    res_ids = last_rows["ids"]
+    res_cnt = last_rows.get("counts")
+    if args.dump_outputs and rank == 0:
+        dumped = dict(last_rows)
+        if ivf:                                      # a row's entries past its count are not part of the answer
+            past = np.arange(topk)[None, :] >= res_cnt[:, None]
+            dumped["ids"] = np.where(past, -1, dumped["ids"])
+            dumped["dists"] = np.where(past, np.float32(np.inf), dumped["dists"])
+        dump_outputs(args.dump_outputs, dumped)
+    if use_dist:
+        elapsed, = max_over_ranks(elapsed)
+    elapsed_g = None
+    if args.full:
+        rows_both_buffers_equal = bool(np.array_equal(host_rows[0][0].numpy(), host_rows[1][0].numpy()))
+        # the same K steps with no timing event at all (twice): what the events attached to the dominant kernel's dispatches cost,
+        # and how stable a K-step sample is
+        plain = [timed_loop(step, args.steps, barrier) for _ in range(2)]
+        # ... with the rows left in HBM (round 3's `value`), and one synchronous device-queries -> host-rows call per step
+        dev_res = timed_loop(step_dev, args.steps, barrier)
+        assert np.array_equal(out_ids.cpu().numpy(), res_ids), "host-delivered rows differ from the device-resident ones"
+        h_i, h_d, h_c = np.empty((B, topk), np.int64), np.empty((B, topk), np.float32), np.empty(B, np.int64)
+
+        def step_sync():
+            if ivf:
+                eng.query_ivf_dev_to_host(my_q.data_ptr(), B, topk, d_tids, S, L, h_i, h_d, h_c, stream)
+            else:
+                eng.query_linear_dev_to_host(my_q.data_ptr(), B, topk, d_tids, S, h_i, h_d, stream)
+
+        for _ in range(max(args.warmup, 1)):
+            step_sync()
+        sync_call = timed_loop(step_sync, args.steps, barrier)
+        assert np.array_equal(h_i, res_ids)
+        if use_dist:
+            preheat_count(step_gather, torch.cuda.synchronize, 100)
+            for _ in range(args.warmup):
+                step_gather()
+            elapsed_g = timed_loop(step_gather, args.steps, barrier)
+            elapsed_g, plain[0], plain[1], cold, dev_res, sync_call = max_over_ranks(elapsed_g, plain[0], plain[1], cold, dev_res, sync_call)
+            allq = gathered[0][0]                        # the gathered batch really is every rank's rows, in rank order
+            assert allq.shape[0] == B * world and torch.equal(allq[rank * B:(rank + 1) * B].to(out_ids.device), out_ids)
 
     # ---------------- strong scaling: BASELINE's "batch=1024 at 1/2/4/8 GPU" -- ONE global batch split over the ranks ----------------
     strong = None
@@ -1356,8 +1438,8 @@ def main():
     if ivf:
         kernel = "ivf_fused" if eng.get_option("ivf_fused") else "ivf_scan"
     k_ms, k_n = dom[kernel]
-    recall = bd.recall_at_r(res_ids, my_gt, 1)
-    if use_dist:
+    recall = bd.recall_at_r(res_ids, my_gt, 1) if args.full else None
+    if use_dist and args.full:
         r = torch.tensor([recall], dtype=torch.float64, device="cpu" if host_coll else dev)
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
         recall = float(r.item()) / world
@@ -1503,30 +1585,35 @@ def main():
                                       "owning rank), with_gather: RCCL all-gather of the result rows in the timed region; "
                                       "strong: ONE global batch of %d split over the ranks" % (world, B),
                        "lut_mode": args.lut_mode, "simd_order": arch,
-                       "scan_mode": "8-bit filter + exact fp32 re-rank" if args.scan_mode else "exact fp32 scan"},
-            "recall_at_1": recall,
-            "results": {"delivery": "host: the last kernel of every timed step writes its rows (ids int64, dists f32%s) straight into pinned host "
-                                    "memory (two buffers in rotation, %d B per step over PCIe; no D2H copy, no per-step synchronisation); queries "
-                                    "resident in HBM" % (", counts int64" if ivf else "", B * topk * 12 + (8 * B if ivf else 0)),
-                        "rows_checked": "host rows == device-resident rows == reference rows (cpu_baseline.ids_match_gpu); both host "
-                                        "buffers hold the batch's rows: %s" % rows_both_buffers_equal,
-                        "device_resident": {"ms_per_step": dev_res / args.steps * 1e3, "value": B * world * args.steps / dev_res,
-                                            "unit": "queries/s", "what": "the same K steps with the rows left in HBM (round 3's `value`)"},
-                        "sync_call": {"ms_per_step": sync_call / args.steps * 1e3, "value": B * world * args.steps / sync_call, "unit": "queries/s",
-                                      "what": "one rii_query_%s_dev_to_host call per step: queries in HBM, rows in the caller's host arrays when "
-                                              "EACH call returns (one host wait per step: nothing of step i+1 is enqueued before step i "
-                                              "has landed)" % ("ivf" if ivf else "linear")}},
-            "roofline": roof,
-            "preheat": {"seconds": PREHEAT_S, "what": "untimed steps before the W warm-up steps: the shader clock ramps over the first ~30 ms "
-                                                        "of sustained load (profiles/r03_clock_ramp.json); `value` is the steady state",
-                        "cold_start_ms_per_step": cold / args.steps * 1e3,
-                        "cold_start_value": B * world * args.steps / cold,
-                        "cold_start_what": "W warm-up + K timed steps issued right after the index build, before any pre-heat"},
-            "uninstrumented": {"ms_per_step": [p_ / args.steps * 1e3 for p_ in plain],
-                               "value": B * world * args.steps / min(plain), "unit": "queries/s",
-                               "what": "the same K steps twice more with no timing event in the stream (`value`'s loop carries two "
-                                       "events on the dominant kernel's dispatch, which the roofline needs)"},
-        }
+                       "scan_mode": "8-bit filter + exact fp32 re-rank" if args.scan_mode else "exact fp32 scan"}}
+        if args.full:
+            line.update({
+                "recall_at_1": recall,
+                "results": {"delivery": "host: the last kernel of every timed step writes its rows (ids int64, dists f32%s) straight into pinned host "
+                                        "memory (two buffers in rotation, %d B per step over PCIe; no D2H copy, no per-step synchronisation); queries "
+                                        "resident in HBM" % (", counts int64" if ivf else "", B * topk * 12 + (8 * B if ivf else 0)),
+                            "rows_checked": "host rows == device-resident rows == reference rows (cpu_baseline.ids_match_gpu); both host "
+                                            "buffers hold the batch's rows: %s" % rows_both_buffers_equal,
+                            "device_resident": {"ms_per_step": dev_res / args.steps * 1e3, "value": B * world * args.steps / dev_res,
+                                                "unit": "queries/s", "what": "the same K steps with the rows left in HBM (round 3's `value`)"},
+                            "sync_call": {"ms_per_step": sync_call / args.steps * 1e3, "value": B * world * args.steps / sync_call, "unit": "queries/s",
+                                          "what": "one rii_query_%s_dev_to_host call per step: queries in HBM, rows in the caller's host arrays when "
+                                                  "EACH call returns (one host wait per step: nothing of step i+1 is enqueued before step i "
+                                                  "has landed)" % ("ivf" if ivf else "linear")}},
+            })
+        line["roofline"] = roof
+        if args.full:
+            line.update({
+                "preheat": {"seconds": PREHEAT_S, "what": "untimed steps before the W warm-up steps: the shader clock ramps over the first ~30 ms "
+                                                            "of sustained load (profiles/r03_clock_ramp.json); `value` is the steady state",
+                            "cold_start_ms_per_step": cold / args.steps * 1e3,
+                            "cold_start_value": B * world * args.steps / cold,
+                            "cold_start_what": "W warm-up + K timed steps issued right after the index build, before any pre-heat"},
+                "uninstrumented": {"ms_per_step": [p_ / args.steps * 1e3 for p_ in plain],
+                                   "value": B * world * args.steps / min(plain), "unit": "queries/s",
+                                   "what": "the same K steps twice more with no timing event in the stream (`value`'s loop carries two "
+                                           "events on the dominant kernel's dispatch, which the roofline needs)"},
+            })
         if elapsed_g is not None:
             line["with_gather"] = {"ms_per_step": elapsed_g / args.steps * 1e3, "value": B * world * args.steps / elapsed_g,
                                    "unit": "queries/s", "backend": dist.get_backend(),

@@ -286,20 +286,24 @@ def _try_import_ref(subdir):
 
 _REF = {}
 
+# "fixed": the builds whose arithmetic their flags determine (v4, else v3 on a host without AVX-512), for the bit-exact tests;
+# the native build's auto-vectorisation follows the build host's -mtune (oracle/Makefile)
+_ORDER = {"native": ["native", "v3"], "v3": ["v3", "native"], "v4": ["v4", "v3"], "fixed": ["v4", "v3"]}
+
 
 def load_reference(prefer="native"):
     """Returns (module `main`, simd_arch string, flavour) or (None, None, None) when no build is usable."""
-    if "r" in _REF:
-        return _REF["r"]
     prefer = os.environ.get("RII_REF_FLAVOUR", prefer)
-    order = ["native", "v3"] if prefer == "native" else ["v3", "native"]
-    for sub in order:
-        mod = _try_import_ref(sub)
+    if prefer in _REF:
+        return _REF[prefer]
+    for sub in _ORDER.get(prefer, _ORDER["v3"]):
+        mod = _REF.get("mod:" + sub) or _try_import_ref(sub)
         if mod is not None:
+            _REF["mod:" + sub] = mod
             # the fvec_L2sqr variant is fixed at *compile* time (recorded by the Makefile)
             with open(os.path.join(_HERE, "_ref", sub, "ARCH")) as f:
                 arch = f.read().strip()
-            _REF["r"] = (mod, arch, sub)
-            return _REF["r"]
-    _REF["r"] = (None, None, None)
-    return _REF["r"]
+            _REF[prefer] = (mod, arch, sub)
+            return _REF[prefer]
+    _REF[prefer] = (None, None, None)
+    return _REF[prefer]

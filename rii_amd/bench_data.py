@@ -64,13 +64,18 @@ def train_pq(train, M, Ks=256, iters=10, seed=123, device=None):
     cw = torch.empty((M, Ks, Ds), dtype=torch.float32, device=dev)
     for m in range(M):
         sub = x[:, m * Ds:(m + 1) * Ds].contiguous()
+        sub_h = sub.cpu().numpy().astype(np.float64)
         cent = sub[torch.randperm(N, generator=g)[:Ks].to(dev)].clone()
         for _ in range(iters):
-            lab = torch.cdist(sub, cent).argmin(1)
-            sums = torch.zeros_like(cent).index_add_(0, lab, sub)
-            cnt = torch.zeros(Ks, device=dev).index_add_(0, lab, torch.ones(N, device=dev))
+            lab = torch.cdist(sub, cent).argmin(1).cpu().numpy()
+            # the centroid sums on the host, in a fixed order: a device index_add_ adds with atomics, in an order that changes
+            # from run to run, and the codebooks (so the benchmark's inputs) with it
+            cnt = np.bincount(lab, minlength=Ks)
+            sums = np.stack([np.bincount(lab, weights=sub_h[:, d], minlength=Ks) for d in range(Ds)], 1)
             nz = cnt > 0
-            cent[nz] = sums[nz] / cnt[nz, None]
+            cent_h = cent.cpu().numpy()
+            cent_h[nz] = (sums[nz] / cnt[nz, None]).astype(np.float32)
+            cent = torch.from_numpy(cent_h).to(dev)
         cw[m] = cent
     return cw.cpu().numpy()
 

@@ -18,9 +18,9 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def reference():
-    """The real reference build (oracle/_ref); tests that need it skip when it is absent/unloadable."""
+    """The real reference build (oracle/_ref) with fixed compiler flags; tests that need it skip when it is absent/unloadable."""
     from oracle import oracle as O
-    mod, arch, flav = O.load_reference()
+    mod, arch, flav = O.load_reference("fixed")
     if mod is None:
         pytest.skip("oracle/_ref not built (needs /root/reference; run `make -C oracle ref`)")
     return mod, arch, flav

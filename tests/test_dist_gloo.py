@@ -645,7 +645,7 @@ def test_bench_runs_under_torchrun_world1_with_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--n-base", "100000", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240)
+                          "--n-base", "100000", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -665,7 +665,7 @@ def _bench_two_ranks(cmd_prefix, extra_env, world=2, n_base=100000, batch=1024, 
     env = dict(os.environ, RII_BENCH_BACKEND="gloo", RII_BENCH_DEVICE="0", **extra_env)
     env.pop("WORLD_SIZE", None)
     cmd = cmd_prefix(sys.executable, os.path.join(root, "bench.py")) + ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--n-base",
-                                                                        str(n_base), "--batch", str(batch), "--no-cpu-baseline"]
+                                                                        str(n_base), "--batch", str(batch), "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -776,7 +776,7 @@ def test_bench_default_line_carries_every_baseline_config():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OMP_NUM_THREADS")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n-base", "200000", "--steps", "3", "--warmup", "1",
-                          "--deep-shard", "400000", "--preheat", "0.02"], env=env, capture_output=True, text=True, timeout=400)
+                          "--deep-shard", "400000", "--preheat", "0.02", "--full"], env=env, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-3000:]
     printed = [l for l in out.stdout.splitlines() if l.strip()]
     assert printed[-1].startswith("{") and len([l for l in printed if l.startswith("{")]) == 1, printed[-3:]

@@ -421,7 +421,7 @@ def test_gpu_state_loads_into_the_real_reference():
     """f2, other direction: an index built on the GPU, handed to the compiled reference (oracle/_ref) through its own
     py::pickle set-state, answers identically there."""
     from rii_amd import RiiGpu
-    ref, arch, _ = O.load_reference()
+    ref, arch, _ = O.load_reference("fixed")
     if ref is None:
         pytest.skip("no runnable oracle/_ref build on this host")
     cw, codes, qs = make_problem(31, 8, 64, 4, 4000, "unit", dup=300)

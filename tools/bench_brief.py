@@ -3,7 +3,7 @@
 kernel, per-kernel shares.   tools/bench_brief.py --topk 10"""
 import json, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-others", "--no-host-call", "--no-fresh", "--no-pipelined"] + sys.argv[1:]
+cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-others", "--no-host-call", "--no-fresh", "--no-pipelined"] + sys.argv[1:]
 out = subprocess.run(cmd, capture_output=True, text=True)
 lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not lines:
