@@ -325,6 +325,9 @@ int rii_fscan_lane_subspace(int M, int lane, int t);
  *                      0 = on the vector ALU (fscan_kernel)
  *   "scan_pipe"        the top-1 scan of M = 16 (one tile per block) / 32 with unsigned table bytes judges a group's sums one group late,
  *                      behind the next group's matrix instructions: 1 = for batches of at most 128 queries [default], 2 = always, 0 = never
+ *   "scan_cascade"     the top-1 scan of M = 32 with unsigned table bytes bounds every group by the sums of its first 16 subspaces and
+ *                      finishes only the groups that pass (fscan_mx_kernel_cascade): 1 = for batches of more than 128 queries
+ *                      that scan at least 2^18 codes [default], 2 = always, 0 = never
  *   "scan_dual"        M = 16: 1 = two 16-query tiles per scan block (fscan_mx_dual_kernel) [default], 0 = one
  *   "scan_order"       1 = the shapes without the rotated table layout scan an LDS-friendly permutation of the codes [default], 0 = id order
  *   "scan_chunks"      chunks of the code array per query tile (grid.x of the scan kernels); 0 = automatic [default]

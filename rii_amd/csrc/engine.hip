@@ -234,6 +234,13 @@ struct rii_engine : ScratchSet {
     // waves of the SIMD already fill the matrix pipe's latency and the longer-lived accumulators cost a little.  1 = batches of at most 128
     // queries [default], 2 = always, 0 = never
     int scan_pipe = 1;
+    // option "scan_cascade": top-1 of M = 32 with unsigned table bytes takes the half sums of every group first and finishes only
+    // the groups where some (query, code) pair passes that bound (fscan_mx_kernel_cascade).  1 = batches of more than 128 queries
+    // over at least kCascadeMinCodes scanned codes [default], 2 = always, 0 = never.  Same-box A/B at B = 1024 (scan kernel,
+    // profiles/r07_cascade_ab.json): N = 1M 0.310 -> 0.268 ms, 500 k 0.162 -> 0.145, 250 k 0.088 both, 100 k 0.045 -> 0.051 (a
+    // chunk-block's few trips run mostly on the loose early thresholds, which send more groups through the finish path); B = 256
+    // at 1M 0.090 -> 0.079; B <= 128 keeps the scan_pipe kernel.
+    int scan_cascade = 1;
     int scan_dual = 1;          // option "scan_dual": M = 16 keeps two 16-query tiles per scan block (fscan_mx_dual_kernel)
     int64_t scan_cov = 0;       // codes [0, scan_cov) are final (whole windows)
     int64_t scan_N = -1;        // N the order was last completed for
@@ -596,6 +603,7 @@ void pick_chunks(const rii_engine *e, int64_t n_codes, int64_t B, int *chunks, i
 }
 
 constexpr int64_t kScanOrderMinN = 1 << 16;     // below this the scan is too short for the order to matter
+constexpr int64_t kCascadeMinCodes = 1 << 18;   // option scan_cascade = 1: shorter scans keep fscan_mx_kernel (see the option)
 
 int ensure_scan_order(rii_engine *e, hipStream_t st)
 {
@@ -849,7 +857,8 @@ int scan_topk(rii_engine *e, const float *d_queries, int64_t B, int topk, const 
                                          (int) B, chunks, len, e->s_cand.as<unsigned long long>(),
                                          e->s_cand_cnt.as<unsigned int>(), cap, 0, nullptr, nullptr,
                                          e->s_gthr.as<uint32_t>(), 1, e->scan_mx, st, e->qlut_quarter ? 1 : 0, e->scan_dual, e->qlut_levels,
-                                         tail_rr ? &tl : nullptr, e->scan_pipe == 2 || (e->scan_pipe == 1 && B <= 128)));
+                                         tail_rr ? &tl : nullptr, e->scan_pipe == 2 || (e->scan_pipe == 1 && B <= 128),
+                                         e->scan_cascade == 2 || (e->scan_cascade == 1 && B > 128 && n_codes >= kCascadeMinCodes)));
                 }
                 if (tail_rr) return RII_OK;
                 ScopedTimer t(e, "rerank", st);
@@ -3091,6 +3100,9 @@ RII_API int rii_set_option(rii_engine *e, const char *key, int64_t value)
     } else if (k == "scan_pipe") {
         if (value < 0 || value > 2) return set_err(RII_ERR_INVALID, "scan_pipe must be 0 (never), 1 (batches <= 128) or 2 (always)");
         e->scan_pipe = (int) value;
+    } else if (k == "scan_cascade") {
+        if (value < 0 || value > 2) return set_err(RII_ERR_INVALID, "scan_cascade must be 0 (never), 1 (batches > 128, scans >= 2^18 codes) or 2 (always)");
+        e->scan_cascade = (int) value;
     } else if (k == "scan_dual") {
         e->scan_dual = value ? 1 : 0;
     } else if (k == "slice_topk") {
@@ -3148,6 +3160,7 @@ RII_API int64_t rii_get_option(const rii_engine *e, const char *key)
     if (k == "scan_mx") return e->scan_mx;
     if (k == "scan_dual") return e->scan_dual;
     if (k == "scan_pipe") return e->scan_pipe;
+    if (k == "scan_cascade") return e->scan_cascade;
     if (k == "small_topk") return e->small_topk;
     if (k == "fused_rerank") return e->fused_rerank;
     if (k == "host_zero_copy") return e->host_zero_copy;

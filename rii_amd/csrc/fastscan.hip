@@ -2493,6 +2493,275 @@ __global__ __launch_bounds__(kFsThreads) void fscan_mx_kernel(FsArgs p)
 }
 
 // =====================================================================================================================
+// fscan_mx_kernel_cascade: the top-1 filter scan of M = 32 (Ks = 256, 16-query tiles, unsigned table bytes) in two passes per
+// group of 16 codes.
+//
+// Every table level is >= 0 (unsigned bytes: 63 / 127 levels), so the sum over any subset of the subspaces is a lower bound of
+// the full sum a(n).  A lane's lookups t = 0 .. 3 (dword w.x of its formatted lookups) are its four rows of half 0; the four
+// lanes g = 0 .. 3 of a column together cover subspaces 0 .. 15 of their code.  The hot loop forms only those: 4 ds_read_b128
+// and 2 v_smfmac per group instead of 8 and 4.  A code whose half sum already reaches the thresholds of all 16 queries of the
+// tile (a_half >= thr) has a >= thr as well and is not a candidate of the full test either; its sum is above every running
+// minimum, so it could not have lowered a threshold.  Only when some (query, code) pair of the group passes the half test does
+// the wave finish the whole group (lookups t = 4 .. 7 = w.y, compiler-scheduled, accumulated onto the half sums) and judge
+// the full sums with the unchanged judge / emit: the candidates are those of fscan_mx_kernel<8, 0> save for codes the full
+// test rejects, and the exactness argument of the header is unchanged.  On the bench data 12.6 % of the groups are finished
+// (matrix instructions per launch: profiles/r07_cascade_pmc.json).  A finish waits for every row in flight (the LDS returns
+// in order), so it costs the wave a whole pipeline latency: DESIGN_DETAILS 3.1 (ix).
+//
+// Pipeline: four register sets of 4 rows (one per group of a trip) keep 16 row reads in flight per wave, as the two sets of
+// 8 rows of fscan_mx_kernel<8> do: group j of trip k waits for its set (the 12 reads of the other sets and the threshold
+// refresh stay outstanding), runs its two matrix instructions and refills the set with group j of trip k + 1 (lookups q[j],
+// loaded a trip ahead).  The finish path retires every outstanding read with its own, so that nothing it does can touch a
+// register whose load has not landed.  Prologue (staging, warm-up, "first trip judged last", gthr sharing, staged candidates) and
+// tail groups are those of fscan_mx_kernel<8, 0>.
+// =====================================================================================================================
+__global__ __launch_bounds__(kFsThreads) void fscan_mx_kernel_cascade(FsArgs p)
+{
+    constexpr int T = 8, M = 32, QR = 16;
+    typedef typename FsMxW<T>::V W;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, tile = blockIdx.y;
+    constexpr size_t lut_bytes = (size_t) M * 256 * QR;
+    uint32_t *s_thr = reinterpret_cast<uint32_t *>(smem + lut_bytes);                       // [16]
+    uint32_t *s_lcnt = reinterpret_cast<uint32_t *>(smem + lut_bytes + 64);                  // [16] staged, [16] global bases
+    uint32_t *s_slk = reinterpret_cast<uint32_t *>(smem + lut_bytes + 64 + QR * 8);          // [16]
+    unsigned long long *s_lcand = reinterpret_cast<unsigned long long *>(smem + lut_bytes + 64 + QR * 8 + 64);
+    {
+        if (tid < 16) s_slk[tid] = (tile * QR + tid < p.B) ? (uint32_t) p.slack[tile * QR + tid] : 0u;
+        if (p.quarter) {            // quarter tables -> 16-byte rotated rows, as in fscan_mx_kernel
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(p.qlut) + (size_t) tile * 4 * M * 256;
+            const int slot = tid & 15, qq = (tid >> 4) & 3;
+            for (int unit = tid >> 6; unit < M; unit += kFsThreads >> 6) {
+                const int h = unit >> 4, ks0 = (unit & 15) * 16;
+                const uint4 *sp = reinterpret_cast<const uint4 *>(src + ((size_t) qq * M + 16 * h + slot) * 256 + ks0);
+                const uint4 v0 = sp[0], v1 = sp[1], v2 = sp[2], v3 = sp[3];
+                uint32_t *d = reinterpret_cast<uint32_t *>(smem + ((size_t) h * 4096 + (size_t) ks0 * 16 + slot) * 16 + qq * 4);
+                d[0 * 64] = v0.x; d[1 * 64] = v0.y; d[2 * 64] = v0.z; d[3 * 64] = v0.w;
+                d[4 * 64] = v1.x; d[5 * 64] = v1.y; d[6 * 64] = v1.z; d[7 * 64] = v1.w;
+                d[8 * 64] = v2.x; d[9 * 64] = v2.y; d[10 * 64] = v2.z; d[11 * 64] = v2.w;
+                d[12 * 64] = v3.x; d[13 * 64] = v3.y; d[14 * 64] = v3.z; d[15 * 64] = v3.w;
+            }
+        } else {
+            const uint4 *s4 = reinterpret_cast<const uint4 *>(p.qlut + (size_t) tile * lut_bytes);
+            uint4 *d4 = reinterpret_cast<uint4 *>(smem);
+            for (size_t i = tid; i < lut_bytes / 16; i += kFsThreads) d4[i] = s4[i];
+        }
+        if (tid < 16) s_thr[tid] = (tile * QR + tid < p.B) ? 0xffffu : 0u;     // queries past the end of the batch never hit
+        if (tid < 2 * QR) s_lcnt[tid] = 0u;
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6, col = lane & 15, gq = lane >> 4;      // this lane judges queries 4 gq .. 4 gq + 3
+    v4i_t spa;
+    int spidx;
+    fs_mx_pattern(col, spa, spidx);
+    uint32_t Ch[4];                                         // address parts of lookups t = 0 .. 3 (w.x, half 0)
+    fs_mx_consts<4>(lane, Ch);
+    // the other address parts are rebuilt where they are used (warm-up / tail groups, the finish path) from a laundered lane
+    // index: kept live through the hot loop, they cost it its spill-free allocation
+    auto lane_now = [&]() {
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        return l;
+    };
+
+    const int64_t c_begin = (int64_t) blockIdx.x * p.chunk_len;
+    int64_t c_end = c_begin + p.chunk_len;
+    if (c_end > p.n_codes) c_end = p.n_codes;
+    const int64_t span = c_end > c_begin ? c_end - c_begin : 0;
+    const int full = (int) (span / kFsThreads);
+    const int tail_groups = (int) ((span - (int64_t) full * kFsThreads + 15) / 16);
+    const W *fc = reinterpret_cast<const W *>(p.codes) + (size_t) (c_begin / 16) * 64 + lane;
+
+    auto emit = [&](int q, uint32_t a, uint32_t t, uint32_t n) {
+        const int b = tile * QR + q;
+        if (b >= p.B) return;
+        const uint32_t nt = fs_thr_of(a, s_slk[q]);
+        if (nt < t) {
+            atomicMin(&s_thr[q], nt);
+            atomicMin(&p.gthr[b], nt);
+        }
+        const unsigned long long rec = ((unsigned long long) a << 32) | n;
+        bool staged = false;
+        if (p.lcap > 0) {
+            const unsigned int lp = atomicAdd(&s_lcnt[q], 1u);
+            if (lp < (unsigned int) p.lcap) { s_lcand[(size_t) q * p.lcap + lp] = rec; staged = true; }
+        }
+        if (!staged) {
+            const unsigned int pos = atomicAdd(&p.cand_count[b], 1u);
+            if (pos < (unsigned int) p.cap) p.cand[(size_t) b * p.cap + pos] = rec;
+        }
+    };
+    auto judge = [&](const v4i_t &acc, const v4i_t &thr, uint32_t n) {
+        const bool h0 = acc[0] < thr[0], h1 = acc[1] < thr[1], h2 = acc[2] < thr[2], h3 = acc[3] < thr[3];
+        if (h0 | h1 | h2 | h3) {
+            uint32_t mask = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u) | (h3 ? 8u : 0u);
+            while (mask) {
+                const int r = __ffs((int) mask) - 1;
+                mask &= mask - 1u;
+                const int a = r == 0 ? acc[0] : r == 1 ? acc[1] : r == 2 ? acc[2] : acc[3];
+                const int t = r == 0 ? thr[0] : r == 1 ? thr[1] : r == 2 ? thr[2] : thr[3];
+                emit(4 * gq + r, (uint32_t) a, (uint32_t) t, n);
+            }
+        }
+    };
+    v4i_t keep = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
+    auto take_min = [&](const v4i_t &acc) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) keep[r] = acc[r] < keep[r] ? acc[r] : keep[r];
+    };
+    auto publish = [&]() {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int v = keep[r];
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1) {
+                const int o = __shfl_xor(v, off);
+                v = o < v ? o : v;
+            }
+            const int b = tile * QR + 4 * gq + r;
+            if (col == 0 && v != 0x7fffffff && b < p.B) atomicMin(&s_thr[4 * gq + r], fs_thr_of((uint32_t) v, s_slk[4 * gq + r]));
+        }
+    };
+    auto load_thr = [&]() { return *reinterpret_cast<const v4i_t *>(s_thr + 4 * gq); };
+    auto adopt = [&](bool first) {
+        int q = tid;
+        asm volatile("" : "+v"(q));         // (addresses rebuilt here, as the address parts above)
+        if (q < QR) {
+            const int b = tile * QR + q;
+            if (b < p.B) {
+                const uint32_t g = __hip_atomic_load(&p.gthr[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (first) {
+                    const uint32_t mine = s_thr[q];
+                    if (mine < g) atomicMin(&p.gthr[b], mine);
+                }
+                atomicMin(&s_thr[q], g);
+            }
+        }
+    };
+    // one group with all 8 lookups (warm-up, tail)
+    auto slow_group = [&](int64_t gi, bool minima, const v4i_t &thr) {
+        const int l = lane_now();
+        const W w = (reinterpret_cast<const W *>(p.codes) + (size_t) (c_begin / 16) * 64 + l)[(size_t) gi * 64];
+        uint32_t C[T];
+        fs_mx_consts<T>(l, C);
+        v4i_t r[T];
+        fs_mx_issue<T>(w, C, r);
+        v4i_t acc = fs_mx_reduce<T>(r, spa, spidx);
+        const int64_t n = c_begin + gi * 16 + col;
+        if (n >= c_end) acc = v4i_t{0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
+        if (minima) take_min(acc);
+        else judge(acc, thr, (uint32_t) n);
+    };
+    auto tail = [&](bool minima) {
+        const v4i_t thr = load_thr();
+        for (int gi = wave; gi < tail_groups; gi += kFsThreads / 64) slow_group((int64_t) full * 64 + gi, minima, thr);
+    };
+
+    // warm-up: the minima of the chunk's first trip (or of the tail) become the first thresholds; that trip is judged last
+    if (full > 0) {
+        const v4i_t none = {0, 0, 0, 0};
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) slow_group(wave * 4 + j, true, none);
+    } else {
+        tail(true);
+    }
+    publish();
+    __syncthreads();
+    adopt(true);
+    __syncthreads();
+
+    const int ntrip = full;
+    auto trip_of = [&](int k) { return k + 1 < full ? k + 1 : 0; };
+    if (ntrip > 0) {
+        const W *pw = fc + (size_t) wave * 4 * 64;
+        auto trip_ptr = [&](int k) { return pw + (size_t) trip_of(k < ntrip ? k : ntrip - 1) * 64 * 64; };   // past the end: valid, unused
+        constexpr int S = 64 * (int) sizeof(W);                 // bytes between the lookups of consecutive groups
+        v4i_t r0[4], r1[4], r2[4], r3[4];                      // the half-0 rows of groups 0 .. 3 of a trip
+        W q[4];                                                 // lookups of group j of the NEXT trip
+        uint32_t y[4];                                          // half-1 lookups (w.y) of group j of THIS trip
+        {
+            const W *p0 = trip_ptr(0), *p1 = trip_ptr(1);
+            const W g0 = p0[0], g1 = p0[64], g2 = p0[128], g3 = p0[192];
+            fs_mx_issue_hot<4>(g0.x, Ch, r0);
+            fs_mx_issue_hot<4>(g1.x, Ch, r1);
+            fs_mx_issue_hot<4>(g2.x, Ch, r2);
+            fs_mx_issue_hot<4>(g3.x, Ch, r3);
+            y[0] = g0.y; y[1] = g1.y; y[2] = g2.y; y[3] = g3.y;
+            fs_mx_load<0>(q[0], p1);                            // in the order of their use: every use has three younger loads behind it
+            fs_mx_load<S>(q[1], p1);
+            fs_mx_load<2 * S>(q[2], p1);
+            fs_mx_load<3 * S>(q[3], p1);
+        }
+        const uint32_t thr_addr = (uint32_t) (lut_bytes + 16 * gq);
+        v4i_t thr;
+        asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(thr) : "v"(thr_addr));
+        // group j of a trip: half sums from set r (waited for: the 12 reads of the other sets and the threshold refresh, 13 in
+        // all, stay outstanding; fewer outstanding only make the wait stricter), set r refilled with the next trip's group j
+        auto group = [&](v4i_t (&r)[4], W &qj, uint32_t &yj, const W *pnn, auto off, uint32_t n) {
+            constexpr int OFF = decltype(off)::value;
+            fs_mx_vmwait<3>(qj);
+            fs_mx_wait<13>(r);
+            v4i_t acc = fs_mx_reduce_refill<4, true>(r, qj.x, Ch, spa, spidx, spa);     // (Z0: the last argument is not read)
+            const uint32_t yh = yj;
+            // keep the half-1 lookups of the next trip's group and reload q[j], in one asm: as two statements the allocator moved
+            // q[j] to a fresh register pair at the top of the loop -- a copy made while its load is still outstanding
+            asm volatile("v_mov_b32 %1, %2\n\tglobal_load_dwordx2 %0, %3, off offset:%4" : "=v"(qj), "=&v"(yj) : "v"(qj.y), "v"(pnn), "n"(OFF));
+            const bool h = (acc[0] < thr[0]) | (acc[1] < thr[1]) | (acc[2] < thr[2]) | (acc[3] < thr[3]);
+            if (__builtin_amdgcn_ballot_w64(h)) {
+                // rare: some pair passed the half test -- finish the group with the lookups of half 1, two rows at a time (the
+                // 16 rows in flight leave 8 registers).  The first two reads queue up behind the rows in flight and one wait
+                // retires them all (draining first and then reading cost one more round trip through the busy LDS)
+                uint32_t Cf[8];
+                fs_mx_consts<8>(lane_now(), Cf);
+                v4i_t f0, f1;
+                fs_mx_issue2<0>(yh, Cf[4], Cf[5], f0, f1);
+                fs_mx_wait<0>(r0); fs_mx_wait<0>(r1); fs_mx_wait<0>(r2); fs_mx_wait<0>(r3);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(thr), "+v"(f0), "+v"(f1));
+                acc = __builtin_amdgcn_smfmac_i32_16x16x128_i8(spa, __builtin_shufflevector(f0, f1, 0, 1, 2, 3, 4, 5, 6, 7), acc, spidx, 0, 0);
+                fs_mx_issue2<2>(yh, Cf[6], Cf[7], f0, f1);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f0), "+v"(f1));
+                acc = __builtin_amdgcn_smfmac_i32_16x16x128_i8(spa, __builtin_shufflevector(f0, f1, 0, 1, 2, 3, 4, 5, 6, 7), acc, spidx, 0, 0);
+                judge(acc, thr, n);
+            }
+        };
+        for (int k = 0; k < ntrip; ++k) {
+            const int it = trip_of(k);
+            const W *pnn = trip_ptr(k + 2);
+            int t_ = tid;
+            asm volatile("" : "+v"(t_));     // (rebuilt every trip, as the address parts above)
+            const uint32_t n = (uint32_t) c_begin + (uint32_t) it * kFsThreads + (uint32_t) (t_ & 0x3cf);     // + 64 wave + col; positions fit 32 bits
+            group(r0, q[0], y[0], pnn, std::integral_constant<int, 0>{}, n);
+            group(r1, q[1], y[1], pnn, std::integral_constant<int, S>{}, n + 16);
+            // thresholds: re-read once per trip into the live registers (any mix of old and new words is a valid set)
+            asm volatile("ds_read_b128 %0, %1 ; rii:inflight-ok (tools/check_isa_inflight.py)" : "+v"(thr) : "v"(thr_addr));
+            group(r2, q[2], y[2], pnn, std::integral_constant<int, 2 * S>{}, n + 32);
+            group(r3, q[3], y[3], pnn, std::integral_constant<int, 3 * S>{}, n + 48);
+            adopt(false);
+        }
+        fs_mx_wait<0>(r0); fs_mx_wait<0>(r1); fs_mx_wait<0>(r2); fs_mx_wait<0>(r3);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(thr));
+        fs_mx_vmwait<0>(q[0]); fs_mx_vmwait<0>(q[1]); fs_mx_vmwait<0>(q[2]); fs_mx_vmwait<0>(q[3]);
+    }
+    tail(false);
+
+    if (p.lcap > 0) {
+        __syncthreads();
+        if (tid < QR) {
+            const int b = tile * QR + tid;
+            const unsigned int c = min(s_lcnt[tid], (unsigned int) p.lcap);
+            s_lcnt[QR + tid] = (c && b < p.B) ? atomicAdd(&p.cand_count[b], c) : 0u;
+        }
+        __syncthreads();
+        for (int q = tid >> 6; q < QR; q += kFsThreads >> 6) {
+            const int b = tile * QR + q;
+            const unsigned int c = min(s_lcnt[q], (unsigned int) p.lcap), base = s_lcnt[QR + q];
+            for (unsigned int i = tid & 63; i < c; i += 64)
+                if (base + i < (unsigned int) p.cap) p.cand[(size_t) b * p.cap + base + i] = s_lcand[(size_t) q * p.lcap + i];
+        }
+    }
+}
+
+// =====================================================================================================================
 // fscan_mx_dual_kernel: M = 16 with TWO 16-query tiles resident (round 3).  The byte tables of 16 queries are 64 KiB at M = 16, so
 // fscan_mx_kernel<4> leaves half of the LDS unused and keeps only 8 row reads in flight per wave (two register sets of 4 rows):
 // 0.50 - 0.56 of the LDS row rate against 0.65 for M = 32.  Here a block holds the tables of tiles 2y and 2y + 1 (128 KiB: the
@@ -2859,6 +3128,18 @@ template <int T, int MODE, int QR = 16, bool TAIL = false, bool PIPE = false> st
     return hipGetLastError();
 }
 
+static hipError_t launch_fscan_mx_cascade(const FsArgs &a, int chunks, int tiles, hipStream_t st)
+{
+    const size_t tab = (size_t) a.M * a.Ks * 16 + 64 + 16 * 8 + 64;
+    FsArgs b = a;
+    b.lcap = (int) std::min<size_t>(128, (kFsLdsBytes - tab) / (16 * 8));
+    const size_t smem = tab + 16 * 8 * (size_t) b.lcap;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fscan_mx_kernel_cascade), hipFuncAttributeMaxDynamicSharedMemorySize, (int) smem);
+    if (e != hipSuccess) return e;
+    launch_timed(fscan_mx_kernel_cascade, dim3(chunks, tiles), dim3(kFsThreads), smem, st, b);
+    return hipGetLastError();
+}
+
 template <int MODE> static hipError_t launch_fscan_mode(const FsArgs &a, int chunks, bool rot, bool mx, hipStream_t st)
 {
     const int qr = fastscan_rows(a.M, a.Ks);
@@ -2902,7 +3183,7 @@ template <int MODE> static hipError_t launch_fscan_mode(const FsArgs &a, int chu
 hipError_t launch_fscan(const uint8_t *d_codes, int64_t n_codes, int M, int Ks, const uint8_t *d_qlut,
                         const int32_t *d_slack, int B, int chunks, int64_t chunk_len, unsigned long long *d_cand,
                         unsigned int *d_cand_count, int cap, int mode, uint16_t *d_segmin, const uint32_t *d_thr16,
-                        uint32_t *d_gthr, int sample_stride, int mx, hipStream_t st, int quarter, int dual, int levels, const FsTail *tail, int pipe)
+                        uint32_t *d_gthr, int sample_stride, int mx, hipStream_t st, int quarter, int dual, int levels, const FsTail *tail, int pipe, int cascade)
 {
     // d_codes: formatted lookups (launch_fcodes_format, same `mx`) for fs_rot_supported shapes, the plain codes otherwise
     if (B == 0 || n_codes == 0) return hipSuccess;
@@ -2921,6 +3202,8 @@ hipError_t launch_fscan(const uint8_t *d_codes, int64_t n_codes, int M, int Ks, 
     a.codes = d_codes; a.n_codes = n_codes; a.M = M; a.Ks = Ks; a.qlut = d_qlut; a.slack = d_slack; a.B = B;
     a.chunk_len = chunk_len; a.cand = d_cand; a.cand_count = d_cand_count; a.cap = cap; a.segmin = d_segmin;
     a.thr16 = d_thr16;
+    // top-1 of M = 32 (16-query tiles) with unsigned table bytes: half sums first (engine option scan_cascade)
+    if (cascade && mode == 0 && rot && mx && M == 32 && a.bias == 0 && !a.tail.queries) return launch_fscan_mx_cascade(a, chunks, (B + 15) / 16, st);
     if (mode == 1) return launch_fscan_mode<1>(a, chunks, rot, mx != 0, st);
     if (mode == 2) return launch_fscan_mode<2>(a, chunks, rot, mx != 0, st);
     return launch_fscan_mode<0>(a, chunks, rot, mx != 0, st);
